@@ -22,7 +22,7 @@ Workloads (--workload):
       7 records, generated on the device); N>1 finishes pool-sliced
       (dist.finalize_step_sliced: reduce-scatter of the currents, LIF + top
       rows of each rank's 1/N of the pool).
-  Side lines (rank 0, N=1) add `parity` (full-size properties + a bit-exact
+  Side lines (rank 0, N=1) add with --full `parity` (full-size properties + a bit-exact
   oracle compare on a 115 Mbase prefix), a prefix-timed `cpu_baseline` and
   the committed PMC traffic of their count kernels (profiles/pmc_<workload>.json).
 
@@ -35,14 +35,22 @@ before the timed region; timed steps run with no event between kernels
 (stage_timing 3), K1a's duration comes from in-kernel s_memrealtime stamps.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload config2|config4]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU)
+
+A plain run sets up, warms up, times the K steps and prints the headline line
+(metric, value, unit, ms_per_step, config).  --dump-outputs DIR then writes
+what the last timed step left in its handle as DIR/<name>.npy (dump_outputs).
+Everything else below -- the one-in-flight run and K1a's roofline, the step
+with the state written, the event cross-check, parity_ranks, and the rank-0
+extras and side-line extras -- runs only with --full.
 
 Without WORLD_SIZE in the environment, --gpus N > 1 starts N ranks itself
 (torch.distributed.run on 127.0.0.1) before anything touches the GPU.  With
 fewer visible devices than ranks the ranks share devices over gloo (a launch
 rehearsal, labelled as such in config.parallelism; not a throughput figure).
 
-Rank 0 at N=1 adds (config2):
+With --full, rank 0 at N=1 adds (config2):
   cpu_baseline  oracle/nk_oracle.c process_parallel restatement on the WHOLE
                 115 Mbase input, parallel over the 7 records like rayon, and a
                 full bit-compare of its outputs with the timed GPU run;
@@ -287,6 +295,34 @@ def timed(fn, reps: int):
     return min(ts), float(np.median(ts))
 
 
+DUMP_MAX_BYTES = 60_000_000  # --dump-outputs: every file together stays below 64 MB
+
+
+def dump_outputs(path: str, c, state=None) -> None:
+    """--dump-outputs: what a caller reads from handle `c` after the last timed
+    step, as <name>.npy.  Integers go out as float64 (exact: every count is
+    far below 2^53), voltages as float32.  A pool too large for the budget is
+    sampled at fixed, seeded neuron indices (sample_index.npy).  `state`: the
+    per-neuron arrays when they were gathered from pool slices (N > 1)."""
+    os.makedirs(path, exist_ok=True)
+    st = state or {"currents": c.currents(), "spike_counts": c.spike_counts(),
+                   "voltages": c.voltages(), "refractory": c.refractory()}
+    pool = st["currents"].size
+    idx = None
+    if pool * 24 > DUMP_MAX_BYTES:
+        rng = np.random.default_rng(0x4E4B4D52)
+        idx = np.unique(rng.integers(0, pool, DUMP_MAX_BYTES // 32))
+        np.save(os.path.join(path, "sample_index.npy"), idx.astype(np.float64))
+    for name, dt in (("currents", np.float64), ("spike_counts", np.float64),
+                     ("voltages", np.float32), ("refractory", np.float32)):
+        a = st[name] if idx is None else st[name][idx]
+        np.save(os.path.join(path, name + ".npy"), a.astype(dt))
+    top = np.array(c.top_abundant_neurons(20), dtype=np.float64).reshape(-1, 3)
+    np.save(os.path.join(path, "top_neurons.npy"), top)  # rows: neuron, spikes, unique k-mers
+    np.save(os.path.join(path, "totals.npy"),
+            np.array([c.energy.total_spikes(), c.energy_used()], dtype=np.float64))
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -343,7 +379,17 @@ def main() -> int:
     ap.add_argument("--loopback", type=int, default=0,
                     help="N > 1: rehearse the N-rank path on ONE GPU, ranks as threads over the "
                          "library's loopback transport (not a scaling figure)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other measurement and check: the "
+                         "one-in-flight run and the roofline, the state-written steps, the event "
+                         "cross-check, parity_ranks (N > 1), the CPU baselines, end_to_end, "
+                         "exact_counts and the side lines' parity (off: the headline line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results (top neurons, totals, per-neuron "
+                         "state) as DIR/<name>.npy, float32/float64, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.loopback > 1:
         if args.workload not in ("config2", "config5"):
@@ -642,6 +688,72 @@ def rank_main(args, world: int, rank: int, local: int, ctx, lcomm) -> int:
     start_ms = sorted(start_host_s)
     start_ms = (round(start_ms[len(start_ms) // 2] * 1e3, 4), round(start_ms[-1] * 1e3, 4)) \
         if start_ms else None
+    log(f"timed {args.steps} steps: {dt / args.steps * 1e3:.4f} ms/step")
+    # step i ran on handle i % inflight: the last timed step's results
+    last = ctrs[(args.steps - 1) % args.inflight]
+    if args.dump_outputs:
+        # (pool-sliced finish: every rank holds its slice, gathered first)
+        st = ctx.gather_state(last) if dist_on and args.finish == "sliced" and \
+            not args.dist_init_only else None
+        if rank == 0:
+            dump_outputs(args.dump_outputs, last, st)
+            log(f"outputs written to {args.dump_outputs}")
+
+    def headline() -> dict:
+        """The result line of a plain run (--full adds to it)."""
+        ms_step = dt / args.steps * 1e3
+        value = total_kmers / (dt / args.steps) / 1e6 if scaling == "strong" else \
+            world * nk_rank / (dt / args.steps) / 1e6
+        return {
+            "metric": METRIC if args.workload == "config2" else SIDE_METRIC[args.workload],
+            "value": round(value, 3), "unit": "Mk-mers/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "settle_steps": settle,
+            "ms_per_step": round(ms_step, 4),
+            "inflight": args.inflight,
+            "defer_hist": defer_hist,
+            "rehearsal": bool(loop or shared),
+            "start_host_ms_median_max": start_ms,
+            "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "u64",
+            "data": ("synthetic (splitmix64 i.i.d. ACGT, seed 0x4E4B4D52" +
+                     ("^rank, 64x200-bp planted repeats per MB)" if args.workload != "config4"
+                      else ", one global stream sharded by byte range)")),
+            "config": {"workload": workload, "k": k, "kmer_width": args.kmer_width,
+                       "pool_size": pool, "bases_rank0": int(n_bases), "records_rank0": n_recs,
+                       "kmers_rank0": nk_rank, "kmers_total": total_kmers,
+                       "parallelism": f"dp{world}" + (
+                           f" (REHEARSAL, not a scaling figure: {world} ranks as threads of one "
+                           f"process on 1 GPU, the library's loopback transport)" if loop else
+                           f" (rehearsal: {world} ranks on {ndev} GPU, {backend})" if shared else ""),
+                       "finish": args.finish if dist_on else None,
+                       "collectives": ((f"in-library communicator ("
+                                        f"{'nk_finalize_sliced_dist' if args.finish == 'sliced' else 'nk_finalize_dist'})"
+                                        + (" over the loopback transport; host barrier/max between "
+                                           "threads" if loop else
+                                           f" over RCCL; torch.distributed {backend} for bootstrap "
+                                           "and timing"))
+                                       if comm is not None
+                                       else (f"torch.distributed {backend} from Python" if dist_on
+                                             else None))},
+            "step_ms_host": [round((b - a) * 1e3, 4) for a, b in zip([t0] + marks[:-1], marks)],
+            "total_spikes": last.energy.total_spikes(),
+        }
+
+    def close_all() -> None:
+        for c in ctrs:
+            if comm is not None:
+                comm.forget(c)
+            c.close()
+        if comm is not None and not loop:
+            comm.close()
+        if not loop:
+            ctx.close()
+
+    if not args.full:  # the plain run ends here
+        if rank == 0:
+            print(json.dumps(headline()), flush=True)
+        close_all()
+        return 0
+    head = headline() if rank == 0 else None
     # both handles' last batches (same input) gave the same results
     same_inflight = None
     if args.inflight > 1:
@@ -653,7 +765,6 @@ def rank_main(args, world: int, rank: int, local: int, ctx, lcomm) -> int:
     marks1 = []
     _, dt1 = timed(args.steps, 1, marks1) if args.inflight > 1 else (t0, dt)
 
-    log(f"timed {args.steps} steps: {dt / args.steps * 1e3:.4f} ms/step")
     # K1a of every step of the one-at-a-time run (in-kernel stamps), and of
     # handle 1's steps in the overlapped run (the other batch's finish beside it)
     spans = ctr.count_spans(args.steps)
@@ -690,9 +801,6 @@ def rank_main(args, world: int, rank: int, local: int, ctx, lcomm) -> int:
         ctx.barrier()
 
     if rank == 0:
-        ms_step = dt / args.steps * 1e3
-        value = total_kmers / (dt / args.steps) / 1e6 if scaling == "strong" else \
-            world * nk_rank / (dt / args.steps) / 1e6
         sp = [x for x in spans if x > 0]
         k1_ms = float(np.mean(sp)) if sp else (float(np.mean(ev_ms)) if ev_ms else float("nan"))
         k1a_alone_ms = k1_ms  # K1a without K1b (the one-in-flight run)
@@ -736,13 +844,7 @@ def rank_main(args, world: int, rank: int, local: int, ctx, lcomm) -> int:
         frac_h = valu.get("frac_of_hash_only", 0.0)
         bound = "valu" if frac_h >= 0.6 and frac_h >= hbm_frac else ("hbm" if hbm_frac >= 0.6 else "latency")
         out = {
-            "metric": METRIC if args.workload == "config2" else SIDE_METRIC[args.workload],
-            "value": round(value, 3), "unit": "Mk-mers/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "settle_steps": settle,
-            "ms_per_step": round(ms_step, 4),
-            "inflight": args.inflight,
-            "defer_hist": defer_hist,
-            "rehearsal": bool(loop or shared),
+            **head,
             "ms_per_step_one_in_flight": round(dt1 / args.steps * 1e3, 4),
             "ms_per_step_state_written": (round(dt_settle / args.steps * 1e3, 4)
                                           if dt_settle is not None else None),
@@ -752,28 +854,6 @@ def rank_main(args, world: int, rank: int, local: int, ctx, lcomm) -> int:
                                    "without that write (the state is derived on demand, "
                                    "bit-identical when read)"),
             "inflight_handles_same_results": same_inflight,
-            "start_host_ms_median_max": start_ms,
-            "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "u64",
-            "data": ("synthetic (splitmix64 i.i.d. ACGT, seed 0x4E4B4D52" +
-                     ("^rank, 64x200-bp planted repeats per MB)" if args.workload != "config4"
-                      else ", one global stream sharded by byte range)")),
-            "config": {"workload": workload, "k": k, "kmer_width": args.kmer_width,
-                       "pool_size": pool, "bases_rank0": int(n_bases), "records_rank0": n_recs,
-                       "kmers_rank0": nk_rank, "kmers_total": total_kmers,
-                       "parallelism": f"dp{world}" + (
-                           f" (REHEARSAL, not a scaling figure: {world} ranks as threads of one "
-                           f"process on 1 GPU, the library's loopback transport)" if loop else
-                           f" (rehearsal: {world} ranks on {ndev} GPU, {backend})" if shared else ""),
-                       "finish": args.finish if dist_on else None,
-                       "collectives": ((f"in-library communicator ("
-                                        f"{'nk_finalize_sliced_dist' if args.finish == 'sliced' else 'nk_finalize_dist'})"
-                                        + (" over the loopback transport; host barrier/max between "
-                                           "threads" if loop else
-                                           f" over RCCL; torch.distributed {backend} for bootstrap "
-                                           "and timing"))
-                                       if comm is not None
-                                       else (f"torch.distributed {backend} from Python" if dist_on
-                                             else None))},
             "roofline": {"bound": bound,
                          "kernel": ("the count of a step: every batch's K1 (k_part / k_part_gen "
                                     "+ k_split) + K1b (k_bucket_hist)" if cm else
@@ -799,7 +879,6 @@ def rank_main(args, world: int, rank: int, local: int, ctx, lcomm) -> int:
                          "avg_launch_ms_events": round(float(np.mean(ev_ms)), 4) if ev_ms else None,
                          "valu": valu},
             "stage_ms_event_steps": {k2: round(v, 4) for k2, v in stages.items()},
-            "step_ms_host": [round((b - a) * 1e3, 4) for a, b in zip([t0] + marks[:-1], marks)],
             "k1a_ms_steps": [round(x, 4) for x in spans],
             "k1a_ms_steps_overlapped": [round(x, 4) for x in spans2],
             "total_spikes": total_spikes,
@@ -818,14 +897,7 @@ def rank_main(args, world: int, rank: int, local: int, ctx, lcomm) -> int:
             out.update(bench_side.side_extras(args, ctr, d_bases, offsets, n_bases, nk_rank,
                                               dev_idx))
         print(json.dumps(out), flush=True)
-    for c in ctrs:
-        if comm is not None:
-            comm.forget(c)
-        c.close()
-    if comm is not None and not loop:
-        comm.close()
-    if not loop:
-        ctx.close()
+    close_all()
     return 0
 
 

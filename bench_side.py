@@ -1,6 +1,7 @@
 """Side lines of bench.py: BASELINE.json configs 3-5 at their real per-GPU size.
 
-Each line carries, besides its throughput:
+Each line carries, besides its throughput (parity and cpu_baseline with
+bench.py --full only):
   parity        full-size properties that do not need the CPU restatement
                 (sum of currents = N_k, sum of spike counts = total spikes,
                 determinism across handles, linearity over record halves or
@@ -253,6 +254,9 @@ def _config3_run(args, path, fsize, n_reads, nk, k, pool, L, dev, Counter, synth
         log(f"step {i}: {ts[-1] * 1e3:.1f} ms")
     t = float(np.median(ts))
     fst = state_of(g)
+    if args.dump_outputs:
+        from bench import dump_outputs
+        dump_outputs(args.dump_outputs, g)
     g.close()
 
     # the same reads resident in HBM: the device-side rate (no file, no PCIe)
@@ -303,7 +307,7 @@ def _config3_run(args, path, fsize, n_reads, nk, k, pool, L, dev, Counter, synth
     read_gbps = fsize / (time.perf_counter() - t0) / 1e9
 
     par = {}
-    if not args.no_side_parity:
+    if args.full and not args.no_side_parity:
         par["sum_currents"] = [int(fst["currents"].sum(dtype=np.uint64)), nk]
         par["sum_spike_counts"] = [int(fst["spike_counts"].sum(dtype=np.uint64)),
                                    fst["total_spikes"]]

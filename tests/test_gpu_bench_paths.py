@@ -23,9 +23,11 @@ if not torch.cuda.is_available():
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bench(*args):
+def _bench(*args, full=True):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1",
            "--no-cpu-baseline", "--no-extras", "--bases", "20000000", "--settle", "0", *args]
+    if full:  # parity_ranks and the other checks beside the headline
+        cmd.append("--full")
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-3000:]
     line = [ln for ln in out.stdout.strip().splitlines() if ln.startswith("{")][-1]
@@ -43,3 +45,31 @@ def test_bench_multi_rank_path(args, world):
     if world > 1:  # (one rank: nothing to compare across ranks)
         assert d["parity_ranks"]["all_equal"] is True, d["parity_ranks"]
         assert d["rehearsal"] is True
+
+
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """A plain run prints the headline line only and, with --dump-outputs,
+    writes the last timed step's results as float32/float64 .npy files."""
+    np = pytest.importorskip("numpy")
+    d = _bench("--gpus", "1", "--dump-outputs", str(tmp_path), full=False)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in d, key
+    assert d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert len(d["step_ms_host"]) == 3
+    for key in ("roofline", "ms_per_step_one_in_flight", "cpu_baseline", "end_to_end"):
+        assert key not in d, key
+    files = sorted(os.listdir(tmp_path))
+    assert files == ["currents.npy", "refractory.npy", "spike_counts.npy", "top_neurons.npy",
+                     "totals.npy", "voltages.npy"]
+    assert sum(os.path.getsize(tmp_path / f) for f in files) <= 64_000_000
+    a = {f[:-4]: np.load(tmp_path / f) for f in files}
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+    pool = d["config"]["pool_size"]
+    assert all(a[n].shape == (pool,) for n in ("currents", "spike_counts", "voltages",
+                                               "refractory"))
+    assert a["currents"].sum() == d["config"]["kmers_rank0"]
+    assert a["spike_counts"].sum() == a["totals"][0] == d["total_spikes"]
+    assert a["top_neurons"].shape == (20, 3)
+    top = a["top_neurons"]
+    assert all(a["spike_counts"][int(i)] == s for i, s, _ in top)
+    assert top[0, 1] == a["spike_counts"].max()

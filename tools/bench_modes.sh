@@ -6,6 +6,7 @@ mkdir -p gpurun_out
 export TMPDIR=/tmp
 run() {
   local tag=$1; shift
+  set -- --full "$@"  # the stage times are behind --full
   timeout -k 10 300 python bench.py --steps 5 --warmup 2 --no-cpu-baseline "$@" > gpurun_out/bm_$tag.log 2>&1
   local rc=$?
   echo "$tag rc=$rc $(tail -1 gpurun_out/bm_$tag.log | python3 -c 'import sys,json
