@@ -342,6 +342,32 @@ long nk_distinct_kmers(nk_counter *c);
  * input the handle holds). */
 int nk_copy_kmer_per_neuron(nk_counter *c, uint32_t *out, size_t n);
 
+/* The whole of `counts` (the reference's Python binding walks counts.iter(),
+ * src/python.rs:30-36): the table of the last process/accumulate call plus
+ * what nk_process_sequence has added since, exactly what nk_get_counts sees
+ * (counts are the same u32-wrapping sums).  The table: see nk_opts.exact_counts.
+ * After nk_exact_adopt a rank lists the keys it owns.  Nothing is changed: not
+ * the table, kmer_per_neuron, the currents or the neuron state.  A key whose
+ * count wrapped to exactly 0 (2^32 occurrences) is skipped by all three calls:
+ * the table cannot tell it from an unused entry. */
+/* every (key, count) of `counts` with min_count <= count <= max_count, keys
+ * ascending (the reference's order is DashMap iteration order, i.e. none).
+ * Device buffers owned by the handle, valid until its next call; complete on
+ * `stream` (NULL: the handle's stream, waited for).  NK_KMER_128: d_keys holds
+ * *n (lo, hi) pairs, ascending as u128.  min_count > max_count: NK_E_INVALID. */
+int nk_export_counts_device(nk_counter *c, uint32_t min_count, uint32_t max_count,
+                            const uint64_t **d_keys, const uint32_t **d_counts,
+                            size_t *n, void *stream);
+/* the same into host arrays: writes the first min(total, cap) pairs in key
+ * order, returns total (>= 0) or a negative error; cap = 0 with NULL arrays
+ * sizes the result.  NK_KMER_128: keys holds 2 words per pair. */
+long nk_export_counts(nk_counter *c, uint32_t min_count, uint32_t max_count,
+                      uint64_t *keys, uint32_t *counts, size_t cap);
+/* abundance spectrum: hist[j] = number of distinct k-mers whose count is j,
+ * 1 <= j < n_bins - 1; hist[n_bins - 1] = those with count >= n_bins - 1
+ * (the "high" bin of jellyfish histo); hist[0] = 0.  2 <= n_bins <= 2^20. */
+int nk_count_spectrum(nk_counter *c, uint64_t *hist, size_t n_bins);
+
 /* SpikingKmerCounter::simulate_spikes_auto(&mut self) — src/spiking_hash.rs:
  * 697-714.  On x86-64 with AVX2 (the reference's target and an MI355X node's
  * host) that is simulate_spikes_simd (:544-659): `steps` LifNeuron updates of

@@ -33,7 +33,7 @@ EXPORTS = (
     "nk_opts_default", "nk_new", "nk_free", "nk_process_parallel", "nk_process_parallel_device",
     "nk_process_file_streaming", "nk_process_file_parallel", "nk_accumulate_device", "nk_finalize", "nk_top_kmers",
     "nk_merge_top_kmers", "nk_top_abundant_neurons", "nk_get_count", "nk_get_counts",
-    "nk_get_counts128",
+    "nk_get_counts128", "nk_export_counts_device", "nk_export_counts", "nk_count_spectrum",
     "nk_distinct_kmers", "nk_copy_kmer_per_neuron", "nk_process_sequence", "nk_total_spikes",
     "nk_energy_used", "nk_set_steps", "nk_get_steps", "nk_pool_size", "nk_k",
     "nk_use_canonical", "nk_copy_currents", "nk_copy_spike_counts", "nk_copy_voltages",
@@ -129,6 +129,9 @@ def load(share_torch: bool = True):
         "nk_get_count": (C.c_int, [vp, u64, P(u32), P(C.c_int)]),
         "nk_get_counts": (C.c_int, [vp, vp, sz, vp, vp]),
         "nk_get_counts128": (C.c_int, [vp, vp, sz, vp, vp]),
+        "nk_export_counts_device": (C.c_int, [vp, u32, u32, P(vp), P(vp), P(sz), vp]),
+        "nk_export_counts": (C.c_long, [vp, u32, u32, vp, vp, sz]),
+        "nk_count_spectrum": (C.c_int, [vp, vp, sz]),
         "nk_distinct_kmers": (C.c_long, [vp]),
         "nk_copy_kmer_per_neuron": (C.c_int, [vp, vp, sz]),
         "nk_process_sequence": (C.c_int, [vp, vp, sz]),
@@ -182,6 +185,17 @@ def load(share_torch: bool = True):
         f.argtypes = args
     _lib = L
     return L
+
+
+def copy_from_device(dst: int, d_src: int, nbytes: int) -> None:
+    """hipMemcpy device -> host with the HIP runtime the library is bound to
+    (resolved through the library's own dependencies)."""
+    f = load().hipMemcpy
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    rc = f(dst, d_src, nbytes, 2)  # hipMemcpyDeviceToHost
+    if rc != 0:
+        raise NeuroKmerError(NK_E_DEVICE, f"hipMemcpy of {nbytes} bytes failed: hipError {rc}")
 
 
 def last_error() -> str:

@@ -271,6 +271,61 @@ class SpikingKmerCounter:
             check(n)
         return n
 
+    # the whole of `counts` (the reference binding's get_counts(), src/python.rs:30-36)
+    def counts_device(self, min_count: int = 1, max_count: int = 2**32 - 1, stream: int = 0):
+        """-> (device ptr of the keys, device ptr of the u32 counts, n): every
+        (key, count) with min_count <= count <= max_count, keys ascending, in
+        buffers of the handle that stay valid until its next call
+        (kmer_width=128: n (lo, hi) u64 pairs)."""
+        self._check_range(min_count, max_count)
+        kp, cp, n = C.c_void_p(), C.c_void_p(), C.c_size_t()
+        check(self._L.nk_export_counts_device(self._h, min_count, max_count, C.byref(kp),
+                                              C.byref(cp), C.byref(n), stream or None))
+        return (kp.value or 0), (cp.value or 0), n.value
+
+    def counts_arrays(self, min_count: int = 1, max_count: int = 2**32 - 1, cap: Optional[int] = None):
+        """-> (keys, counts u32[n]) of `counts` in key order, counts within
+        [min_count, max_count]; keys is uint64[n], or for kmer_width=128 a list
+        of Python ints.  cap: at most that many pairs (the first in key order)."""
+        self._check_range(min_count, max_count)
+        w = 2 if self.kmer_width == 128 else 1
+        if cap is None:  # one export on the device, then a copy of all of it
+            kp, cp, n = self.counts_device(min_count, max_count)
+            keys = np.zeros(max(w * n, 1), np.uint64)
+            cnt = np.zeros(max(n, 1), np.uint32)
+            if n:
+                _lib.copy_from_device(keys.ctypes.data, kp, 8 * w * n)
+                _lib.copy_from_device(cnt.ctypes.data, cp, 4 * n)
+        else:
+            cap = int(cap)
+            keys = np.zeros(max(w * cap, 1), np.uint64)
+            cnt = np.zeros(max(cap, 1), np.uint32)
+            total = check(self._L.nk_export_counts(self._h, min_count, max_count,
+                                                   keys.ctypes.data if cap else None,
+                                                   cnt.ctypes.data if cap else None, cap))
+            n = min(total, cap)
+        keys, cnt = keys[:w * n], cnt[:n]
+        if w == 2:
+            return [int(keys[2 * i]) | (int(keys[2 * i + 1]) << 64) for i in range(n)], cnt
+        return keys, cnt
+
+    def count_total(self, min_count: int = 1, max_count: int = 2**32 - 1) -> int:
+        """Number of pairs counts_arrays would return (nk_export_counts with cap 0)."""
+        self._check_range(min_count, max_count)
+        return check(self._L.nk_export_counts(self._h, min_count, max_count, None, None, 0))
+
+    def spectrum(self, n_bins: int = 10001) -> np.ndarray:
+        """Abundance spectrum uint64[n_bins]: [j] = distinct k-mers with count
+        j; the last bin takes every count >= n_bins - 1; [0] = 0."""
+        hist = np.zeros(max(int(n_bins), 1), np.uint64)
+        check(self._L.nk_count_spectrum(self._h, hist.ctypes.data, int(n_bins)))
+        return hist
+
+    @staticmethod
+    def _check_range(lo: int, hi: int) -> None:
+        if not (0 <= lo < 2**32 and 0 <= hi < 2**32):
+            raise ValueError("min_count and max_count must fit in 32 bits")
+
     def kmer_per_neuron(self) -> np.ndarray:
         """The full kmer_per_neuron map as a dense u32 array."""
         return self._copy("nk_copy_kmer_per_neuron", np.uint32)

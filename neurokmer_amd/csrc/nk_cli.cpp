@@ -36,6 +36,10 @@ static void usage() {
           "      --canonical\n"
           "      --streaming\n"
           "      --device <N>             HIP device ordinal [default: 0]\n"
+          "      --spectrum <FILE>        Write the abundance spectrum: 'count n_kmers' lines\n"
+          "      --spectrum-max <N>       Largest count with a line of its own [default: 10000]\n"
+          "      --counts <FILE>          Write every k-mer as 'KMER<TAB>count', in key order (k <= 32)\n"
+          "      --min-count <N>          Smallest count --counts writes [default: 1]\n"
           "  -h, --help                   Print help\n");
 }
 
@@ -46,9 +50,54 @@ static bool parse_u64(const char *s, unsigned long long &out) {
   return end && *end == 0;
 }
 
+// --spectrum: one 'count n_kmers' line per non-empty bin, ascending (the last
+// bin holds every count >= spectrum_max + 1, as jellyfish histo's high bin)
+static int write_spectrum(nk_counter *c, const std::string &path, size_t n_bins) {
+  std::vector<uint64_t> hist(n_bins);
+  if (nk_count_spectrum(c, hist.data(), n_bins)) {
+    fprintf(stderr, "Error: %s\n", nk_last_error());
+    return 1;
+  }
+  FILE *f = fopen(path.c_str(), "w");
+  if (!f) {
+    fprintf(stderr, "Error: cannot write %s\n", path.c_str());
+    return 1;
+  }
+  for (size_t j = 1; j < n_bins; ++j)
+    if (hist[j]) fprintf(f, "%zu %llu\n", j, (unsigned long long)hist[j]);
+  return fclose(f) ? 1 : 0;
+}
+
+// --counts: 'KMER<TAB>count' per key in key order; the k-mer is the 2-bit key
+// decoded, first base in the highest bits (A C G T = 0 1 2 3)
+static int write_counts(nk_counter *c, const std::string &path, unsigned k, uint32_t min_count) {
+  long total = nk_export_counts(c, min_count, UINT32_MAX, nullptr, nullptr, 0);
+  if (total < 0) {
+    fprintf(stderr, "Error: %s\n", nk_last_error());
+    return 1;
+  }
+  std::vector<uint64_t> keys((size_t)total);
+  std::vector<uint32_t> cnt((size_t)total);
+  if (total && nk_export_counts(c, min_count, UINT32_MAX, keys.data(), cnt.data(), (size_t)total) < 0) {
+    fprintf(stderr, "Error: %s\n", nk_last_error());
+    return 1;
+  }
+  FILE *f = fopen(path.c_str(), "w");
+  if (!f) {
+    fprintf(stderr, "Error: cannot write %s\n", path.c_str());
+    return 1;
+  }
+  std::string kmer(k, 'A');
+  for (long i = 0; i < total; ++i) {
+    for (unsigned j = 0; j < k; ++j) kmer[j] = "ACGT"[(keys[i] >> (2 * (k - 1 - j))) & 3];
+    fprintf(f, "%s\t%u\n", kmer.c_str(), cnt[i]);
+  }
+  return fclose(f) ? 1 : 0;
+}
+
 int main(int argc, char **argv) {
-  std::string input;
-  unsigned long long k = 31, pool = 1000000, device = 0;
+  std::string input, spectrum_path, counts_path;
+  unsigned long long k = 31, pool = 1000000, device = 0, spectrum_max = 10000, min_count = 1;
   bool canonical = false, streaming = false, have_input = false;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -80,6 +129,14 @@ int main(int argc, char **argv) {
       streaming = true;
     } else if (is("--device")) {
       if (!parse_u64(val("--device <N>"), device)) { fprintf(stderr, "error: invalid value for '--device <N>'\n"); return 2; }
+    } else if (is("--spectrum-max")) {
+      if (!parse_u64(val("--spectrum-max <N>"), spectrum_max) || spectrum_max > (1ull << 20) - 2) { fprintf(stderr, "error: invalid value for '--spectrum-max <N>'\n"); return 2; }
+    } else if (is("--spectrum")) {
+      spectrum_path = val("--spectrum <FILE>");
+    } else if (is("--min-count")) {
+      if (!parse_u64(val("--min-count <N>"), min_count) || min_count > 0xFFFFFFFFull) { fprintf(stderr, "error: invalid value for '--min-count <N>'\n"); return 2; }
+    } else if (is("--counts")) {
+      counts_path = val("--counts <FILE>");
     } else {
       fprintf(stderr, "error: unexpected argument '%s' found\n", a.c_str());
       usage();
@@ -89,6 +146,10 @@ int main(int argc, char **argv) {
   if (!have_input) {
     fprintf(stderr, "error: the following required arguments were not provided:\n  --input <INPUT>\n");
     usage();
+    return 2;
+  }
+  if (!counts_path.empty() && k > 32) {
+    fprintf(stderr, "error: --counts decodes 2-bit keys (k <= 32); the keys of k = %llu are not k-mers\n", k);
     return 2;
   }
   fprintf(stderr, "[INFO neurokmer] Starting NeuroKmer on %s (k=%llu, pool_size=%llu, canonical=%s, streaming=%s)\n",
@@ -144,6 +205,9 @@ int main(int argc, char **argv) {
   printf("Simulated energy used: %s\n", rust_f64(nk_energy_used(c)).c_str());
   printf("Neuron pool size used: %llu\n", pool);
   printf("Streaming mode: %s\n", streaming ? "true" : "false");
+  int out_rc = 0;
+  if (!spectrum_path.empty()) out_rc = write_spectrum(c, spectrum_path, (size_t)spectrum_max + 2);
+  if (!out_rc && !counts_path.empty()) out_rc = write_counts(c, counts_path, (unsigned)k, (uint32_t)min_count);
   nk_free(c);
-  return 0;
+  return out_rc;
 }

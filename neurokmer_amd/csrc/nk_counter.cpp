@@ -339,6 +339,9 @@ void nk_free(nk_counter *c) {
   c->x_keys.release(); c->x_sorted.release(); c->x_uniq.release(); c->x_q.release();
   c->x_cnt.release(); c->x_tile_rec.release(); c->kpn.release(); c->x_out.release();
   c->x_pres.release(); c->x_tmp.release(); c->x_n.release();
+  c->en_k0.release(); c->en_k1.release(); c->en_k2.release(); c->en_c0.release();
+  c->en_c1.release(); c->en_c2.release(); c->en_wg.release(); c->en_n.release();
+  c->en_hist.release(); c->en_tmp.release();
   c->x_ent.release(); c->p_key.release(); c->xg_key.release(); c->xg_key2.release();
   c->xg_side.release(); c->xg_off.release(); c->xg_over.release(); c->xg_cnt.release();
   c->xg_gst.release(); c->xg_trec.release(); c->xg_fill.release(); c->xg_bin2.release();

@@ -192,6 +192,33 @@ hipError_t exact_merge_pairs(const uint64_t *keys, const uint32_t *cnt, size_t n
                              uint32_t *uniq_cnt, unsigned long long *n_uniq, void *tmp,
                              size_t tmp_bytes, hipStream_t s);
 
+// ---- enumeration (nk_enum.hip): nk_export_counts(_device), nk_count_spectrum --
+// The order-preserving range filter over (key, count) arrays of *n entries
+// (n null: max_n; never more than max_n), one workgroup per kEnumTile entries:
+//   enum_filter_count  wg[g] = the tile's entries with lo <= count <= hi, then
+//                      scanned in place to output offsets starting at *at
+//                      (null: 0); *n_out = *at + survivors.  wg: enum_groups(max_n)
+//   enum_filter_write  every survivor to its offset, in entry order (wpk 2:
+//                      keys are (lo, hi) pairs, moved with 16-byte accesses)
+// No global atomic per entry, so a sorted input stays sorted.
+constexpr int kEnumTile = 4096;
+inline size_t enum_groups(size_t max_n) { return (max_n + kEnumTile - 1) / kEnumTile; }
+hipError_t enum_filter_count(const uint32_t *cnt, const unsigned long long *n, size_t max_n,
+                             uint32_t lo, uint32_t hi, unsigned long long *wg,
+                             const unsigned long long *at, unsigned long long *n_out,
+                             hipStream_t s);
+hipError_t enum_filter_write(const uint64_t *keys, const uint32_t *cnt, const unsigned long long *n,
+                             size_t max_n, int wpk, uint32_t lo, uint32_t hi, uint64_t *out_keys,
+                             uint32_t *out_cnt, const unsigned long long *wg, hipStream_t s);
+// the delta's ~0 key (DeltaArgs::meta[0], when non-zero) appended at *n; *n += 1
+hipError_t enum_delta_ones(const unsigned long long *meta, uint64_t *out_keys, uint32_t *out_cnt,
+                           unsigned long long *n, hipStream_t s);
+// hist[min(count, n_bins - 1)] += 1 per entry with a non-zero count (hist
+// zeroed by the caller, n_bins >= 2); counts below kSpecLds in an LDS histogram
+constexpr int kSpecLds = 8192;
+hipError_t enum_spectrum(const uint32_t *cnt, const unsigned long long *n, size_t max_n,
+                         uint32_t n_bins, unsigned long long *hist, hipStream_t s);
+
 // uniques column of the top rows from kmer_per_neuron
 hipError_t exact_top_uniques(const TopCand *cand, uint32_t m, const uint32_t *kpn, uint32_t *uniq,
                              hipStream_t s);

@@ -6,6 +6,7 @@
 //   nk_finish.cpp       LIF, top-N selection, uniques, readback, process calls
 //   nk_export.cpp       the multi-GPU finish pieces (wire, export, merge, slices)
 //   nk_table_host.cpp   the exact k-mer table, process_sequence, extended top rows
+//   nk_enum_host.cpp    the table listed: export of (key, count) pairs, abundance spectrum
 //   nk_ingest_host.cpp  file ingest (device FASTA/FASTQ parse, host FASTQ extraction)
 // Mirrors SpikingKmerCounter (src/spiking_hash.rs:16-715) with all per-neuron
 // state resident in HBM of one MI355X:
@@ -241,6 +242,13 @@ struct nk_counter {
   DevBuf<uint32_t> xp_cnt;
   DevBuf<unsigned long long> xp_ctr;
   DevBuf<uint8_t> x_tmp;
+  // enumeration (nk_enum_host.cpp): gathered / filtered pairs [0], their sort
+  // [1] and merge [2]; filter workgroup offsets; [0] base entries gathered,
+  // [1] + delta, [2] merged keys, [3] filter survivors; the spectrum
+  DevBuf<uint64_t> en_k0, en_k1, en_k2;
+  DevBuf<uint32_t> en_c0, en_c1, en_c2;
+  DevBuf<unsigned long long> en_wg, en_n, en_hist;
+  DevBuf<uint8_t> en_tmp;
   // [0] keys of the last input (sorted build) / of a process_sequence record,
   // [1] table entries (sorted: distinct keys; grouped: span + side part),
   // [2] grouped: first index of the side part, [3] side part's entries,
