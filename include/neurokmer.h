@@ -368,6 +368,44 @@ long nk_export_counts(nk_counter *c, uint32_t min_count, uint32_t max_count,
  * (the "high" bin of jellyfish histo); hist[0] = 0.  2 <= n_bins <= 2^20. */
 int nk_count_spectrum(nk_counter *c, uint64_t *hist, size_t n_bins);
 
+/* Sequences run against `counts`: the abundance of every k-mer along each
+ * record (coverage) and per-record statistics.  A window's count is what
+ * nk_get_counts answers for its key -- the handle's own k, canonical flag and
+ * key width; the table of the last process/accumulate call plus what
+ * nk_process_sequence has added; an absent key counts 0 (so every window of a
+ * fresh or reset handle counts 0).  The table: see nk_opts.exact_counts.
+ * Nothing in the handle is changed, the retained last input included: the
+ * query works in device buffers of its own.  After nk_exact_adopt a rank holds
+ * only the keys it owns: NK_E_UNSUPPORTED. */
+#define NK_COV_NONE 0xFFFFFFFFu /* no k-mer window starts at this base */
+typedef struct nk_read_stats { /* 40 bytes */
+  uint64_t n_kmers;   /* windows of the record: max(0, len - k + 1) */
+  uint64_t n_present; /* windows whose count is >= min_count */
+  uint64_t sum;       /* sum of the windows' counts */
+  uint32_t min, max;  /* over the windows (0 when n_kmers == 0) */
+  uint32_t median;    /* element n_kmers / 2 of the counts sorted ascending (khmer's median) */
+  uint32_t _pad;      /* 0 */
+} nk_read_stats;
+/* The statistics take one of three paths by a record's window count: up to
+ * NK_QUERY_WAVE_MAX a wavefront per record, up to NK_QUERY_BLOCK_MAX a
+ * workgroup per record (counts in LDS), longer records a radix select over HBM. */
+#define NK_QUERY_WAVE_MAX 256
+#define NK_QUERY_BLOCK_MAX 8192
+/* Input layout and limits of nk_process_parallel_device (16-byte aligned
+ * d_bases, n_recs + 1 offsets).  d_cov[p] (n_bases entries, may be NULL) = the
+ * count of the window starting at base p, NK_COV_NONE where none starts (the
+ * last k-1 bases of a record, every base of a record shorter than k);
+ * d_stats (n_recs entries, may be NULL) from the record geometry, never from
+ * that sentinel.  min_count == 0 behaves as 1.  Enqueued on `stream` (NULL: the
+ * handle's stream, waited for).  NK_E_INVALID: both outputs NULL, or null
+ * input with n_recs > 0. */
+int nk_query_abundance_device(nk_counter *c, const uint8_t *d_bases, const uint64_t *d_rec_offsets,
+                              size_t n_recs, size_t n_bases, uint32_t min_count, uint32_t *d_cov,
+                              nk_read_stats *d_stats, void *stream);
+/* the same over host arrays (n_bases = rec_offsets[n_recs]), complete on return */
+int nk_query_abundance(nk_counter *c, const uint8_t *bases, const uint64_t *rec_offsets,
+                       size_t n_recs, uint32_t min_count, uint32_t *cov, nk_read_stats *stats);
+
 /* SpikingKmerCounter::simulate_spikes_auto(&mut self) — src/spiking_hash.rs:
  * 697-714.  On x86-64 with AVX2 (the reference's target and an MI355X node's
  * host) that is simulate_spikes_simd (:544-659): `steps` LifNeuron updates of

@@ -27,6 +27,10 @@ NK_E_UNSUPPORTED = -6
 NK_E_DEVICE = -7
 NK_KMER_COMPAT = 0
 NK_KMER_128 = 1
+NK_COV_NONE = 0xFFFFFFFF  # coverage: no k-mer window starts at this base
+# window counts at which the per-record statistics change path (neurokmer.h)
+NK_QUERY_WAVE_MAX = 256
+NK_QUERY_BLOCK_MAX = 8192
 
 # every symbol include/neurokmer.h declares
 EXPORTS = (
@@ -34,6 +38,7 @@ EXPORTS = (
     "nk_process_file_streaming", "nk_process_file_parallel", "nk_accumulate_device", "nk_finalize", "nk_top_kmers",
     "nk_merge_top_kmers", "nk_top_abundant_neurons", "nk_get_count", "nk_get_counts",
     "nk_get_counts128", "nk_export_counts_device", "nk_export_counts", "nk_count_spectrum",
+    "nk_query_abundance_device", "nk_query_abundance",
     "nk_distinct_kmers", "nk_copy_kmer_per_neuron", "nk_process_sequence", "nk_total_spikes",
     "nk_energy_used", "nk_set_steps", "nk_get_steps", "nk_pool_size", "nk_k",
     "nk_use_canonical", "nk_copy_currents", "nk_copy_spike_counts", "nk_copy_voltages",
@@ -62,6 +67,21 @@ class NkOpts(C.Structure):
 class NkTopRow(C.Structure):
     _fields_ = [("idx", C.c_uint64), ("spikes", C.c_uint64), ("uniques", C.c_uint32),
                 ("_pad", C.c_uint32)]
+
+
+class NkReadStats(C.Structure):
+    _fields_ = [("n_kmers", C.c_uint64), ("n_present", C.c_uint64), ("sum", C.c_uint64),
+                ("min", C.c_uint32), ("max", C.c_uint32), ("median", C.c_uint32),
+                ("_pad", C.c_uint32)]
+
+
+def read_stats_dtype():
+    """numpy mirror of nk_read_stats (itemsize 40, the struct's own offsets)."""
+    import numpy as np
+    return np.dtype({"names": [f[0] for f in NkReadStats._fields_],
+                     "formats": [np.dtype(f[1]) for f in NkReadStats._fields_],
+                     "offsets": [getattr(NkReadStats, f[0]).offset for f in NkReadStats._fields_],
+                     "itemsize": C.sizeof(NkReadStats)})
 
 
 class NeuroKmerError(RuntimeError):
@@ -132,6 +152,8 @@ def load(share_torch: bool = True):
         "nk_export_counts_device": (C.c_int, [vp, u32, u32, P(vp), P(vp), P(sz), vp]),
         "nk_export_counts": (C.c_long, [vp, u32, u32, vp, vp, sz]),
         "nk_count_spectrum": (C.c_int, [vp, vp, sz]),
+        "nk_query_abundance_device": (C.c_int, [vp, vp, vp, sz, sz, u32, vp, vp, vp]),
+        "nk_query_abundance": (C.c_int, [vp, vp, vp, sz, u32, vp, vp]),
         "nk_distinct_kmers": (C.c_long, [vp]),
         "nk_copy_kmer_per_neuron": (C.c_int, [vp, vp, sz]),
         "nk_process_sequence": (C.c_int, [vp, vp, sz]),

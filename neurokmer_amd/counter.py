@@ -321,6 +321,41 @@ class SpikingKmerCounter:
         check(self._L.nk_count_spectrum(self._h, hist.ctypes.data, int(n_bins)))
         return hist
 
+    # sequences against `counts` (include/neurokmer.h: nk_query_abundance)
+    def abundance(self, seqs: Sequence[bytes], min_count: int = 1, coverage: bool = False):
+        """Per-record k-mer abundance statistics of `seqs` against the table:
+        a structured array (n_kmers, n_present, sum, min, max, median; the
+        median is khmer's, element n_kmers // 2 of the sorted counts).
+        coverage=True: -> (stats, cov uint32[n_bases]), cov[p] = the count of
+        the k-mer starting at base p, NK_COV_NONE where none starts."""
+        return self.abundance_arrays(*records_to_arrays(seqs), min_count=min_count,
+                                     coverage=coverage)
+
+    def abundance_arrays(self, bases: np.ndarray, offsets: np.ndarray, min_count: int = 1,
+                         coverage: bool = False):
+        bases = np.ascontiguousarray(bases, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        self._check_range(min_count, min_count)
+        n_recs = max(offsets.size - 1, 0)
+        stats = np.zeros(n_recs, _lib.read_stats_dtype())
+        cov = np.zeros(int(offsets[-1]) if offsets.size else 0, np.uint32) if coverage else None
+        # (a pointer even when empty: a null pair of outputs is an error)
+        check(self._L.nk_query_abundance(self._h, _ptr(bases), _ptr(offsets), n_recs, min_count,
+                                         cov.ctypes.data if coverage else None,
+                                         stats.ctypes.data))
+        return (stats, cov) if coverage else stats
+
+    def abundance_device(self, d_bases: int, d_offsets: int, n_recs: int, n_bases: int,
+                         d_cov: int = 0, d_stats: int = 0, min_count: int = 1,
+                         stream: int = 0) -> None:
+        """The query over device memory (layout of process_parallel_device):
+        d_cov uint32[n_bases] and / or d_stats nk_read_stats[n_recs] (0: not
+        wanted), enqueued on `stream` (0: the handle's stream, waited for)."""
+        self._check_range(min_count, min_count)
+        check(self._L.nk_query_abundance_device(self._h, d_bases or None, d_offsets or None,
+                                                n_recs, n_bases, min_count, d_cov or None,
+                                                d_stats or None, stream or None))
+
     @staticmethod
     def _check_range(lo: int, hi: int) -> None:
         if not (0 <= lo < 2**32 and 0 <= hi < 2**32):

@@ -40,6 +40,9 @@ static void usage() {
           "      --spectrum-max <N>       Largest count with a line of its own [default: 10000]\n"
           "      --counts <FILE>          Write every k-mer as 'KMER<TAB>count', in key order (k <= 32)\n"
           "      --min-count <N>          Smallest count --counts writes [default: 1]\n"
+          "      --query <FILE>           FASTA/FASTQ records to run against the k-mer table\n"
+          "      --query-out <FILE>       Per query record: 'index n_kmers n_present min median max sum' (tabs)\n"
+          "      --query-min-count <N>    Smallest count of a present k-mer [default: 1]\n"
           "  -h, --help                   Print help\n");
 }
 
@@ -95,9 +98,39 @@ static int write_counts(nk_counter *c, const std::string &path, unsigned k, uint
   return fclose(f) ? 1 : 0;
 }
 
+// --query / --query-out: the query file's records (the host reader, plain or
+// gzip) against the table of the run; one line per record, in file order
+static int write_query(nk_counter *c, const std::string &query, const std::string &path,
+                       uint32_t min_count) {
+  std::vector<uint8_t> bases;
+  std::vector<uint64_t> offs;
+  std::string err;
+  if (nk::read_fastx_all(query.c_str(), bases, offs, err)) {
+    fprintf(stderr, "Error: %s\n", err.c_str());
+    return 1;
+  }
+  const size_t n = offs.size() - 1;
+  std::vector<nk_read_stats> st(n);
+  if (nk_query_abundance(c, bases.data(), offs.data(), n, min_count, nullptr, st.data())) {
+    fprintf(stderr, "Error: %s\n", nk_last_error());
+    return 1;
+  }
+  FILE *f = fopen(path.c_str(), "w");
+  if (!f) {
+    fprintf(stderr, "Error: cannot write %s\n", path.c_str());
+    return 1;
+  }
+  for (size_t i = 0; i < n; ++i)
+    fprintf(f, "%zu\t%llu\t%llu\t%u\t%u\t%u\t%llu\n", i, (unsigned long long)st[i].n_kmers,
+            (unsigned long long)st[i].n_present, st[i].min, st[i].median, st[i].max,
+            (unsigned long long)st[i].sum);
+  return fclose(f) ? 1 : 0;
+}
+
 int main(int argc, char **argv) {
-  std::string input, spectrum_path, counts_path;
+  std::string input, spectrum_path, counts_path, query_path, query_out;
   unsigned long long k = 31, pool = 1000000, device = 0, spectrum_max = 10000, min_count = 1;
+  unsigned long long query_min = 1;
   bool canonical = false, streaming = false, have_input = false;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -137,6 +170,12 @@ int main(int argc, char **argv) {
       if (!parse_u64(val("--min-count <N>"), min_count) || min_count > 0xFFFFFFFFull) { fprintf(stderr, "error: invalid value for '--min-count <N>'\n"); return 2; }
     } else if (is("--counts")) {
       counts_path = val("--counts <FILE>");
+    } else if (is("--query-out")) {
+      query_out = val("--query-out <FILE>");
+    } else if (is("--query-min-count")) {
+      if (!parse_u64(val("--query-min-count <N>"), query_min) || query_min > 0xFFFFFFFFull) { fprintf(stderr, "error: invalid value for '--query-min-count <N>'\n"); return 2; }
+    } else if (is("--query")) {
+      query_path = val("--query <FILE>");
     } else {
       fprintf(stderr, "error: unexpected argument '%s' found\n", a.c_str());
       usage();
@@ -150,6 +189,11 @@ int main(int argc, char **argv) {
   }
   if (!counts_path.empty() && k > 32) {
     fprintf(stderr, "error: --counts decodes 2-bit keys (k <= 32); the keys of k = %llu are not k-mers\n", k);
+    return 2;
+  }
+  if (query_path.empty() != query_out.empty()) {
+    fprintf(stderr, "error: --query <FILE> and --query-out <FILE> go together\n");
+    usage();
     return 2;
   }
   fprintf(stderr, "[INFO neurokmer] Starting NeuroKmer on %s (k=%llu, pool_size=%llu, canonical=%s, streaming=%s)\n",
@@ -208,6 +252,7 @@ int main(int argc, char **argv) {
   int out_rc = 0;
   if (!spectrum_path.empty()) out_rc = write_spectrum(c, spectrum_path, (size_t)spectrum_max + 2);
   if (!out_rc && !counts_path.empty()) out_rc = write_counts(c, counts_path, (unsigned)k, (uint32_t)min_count);
+  if (!out_rc && !query_path.empty()) out_rc = write_query(c, query_path, query_out, (uint32_t)query_min);
   nk_free(c);
   return out_rc;
 }

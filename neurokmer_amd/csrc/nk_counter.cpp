@@ -342,6 +342,9 @@ void nk_free(nk_counter *c) {
   c->en_k0.release(); c->en_k1.release(); c->en_k2.release(); c->en_c0.release();
   c->en_c1.release(); c->en_c2.release(); c->en_wg.release(); c->en_n.release();
   c->en_hist.release(); c->en_tmp.release();
+  c->q_bases.release(); c->q_offs.release(); c->q_trec.release(); c->q_cov.release();
+  c->q_stats.release(); c->q_mid.release(); c->q_long.release(); c->q_ctr.release();
+  c->q_acc.release();
   c->x_ent.release(); c->p_key.release(); c->xg_key.release(); c->xg_key2.release();
   c->xg_side.release(); c->xg_off.release(); c->xg_over.release(); c->xg_cnt.release();
   c->xg_gst.release(); c->xg_trec.release(); c->xg_fill.release(); c->xg_bin2.release();

@@ -19,6 +19,8 @@
 #include "nk_device.h"
 #include "nk_kernels.h"
 
+struct nk_read_stats;  // include/neurokmer.h
+
 namespace nk {
 
 // ---- table layouts -----------------------------------------------------------
@@ -145,6 +147,14 @@ struct DeltaArgs {
   uint64_t mask;              // cap - 1
   unsigned long long *meta;   // [0] count of key ~0, [1] keys new to counts (distinct)
 };
+// a free slot's key, and the slot a key's probe starts at (& mask); the key ~0
+// itself is counted in meta[0]
+constexpr unsigned long long kDEmpty = ~0ULL;
+__device__ __forceinline__ uint64_t dmix(uint64_t z) {
+  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
+  z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
+  return z ^ (z >> 31);
+}
 hipError_t delta_clear(const DeltaArgs &d, hipStream_t s);
 hipError_t delta_rehash(const DeltaArgs &from, const DeltaArgs &to, hipStream_t s);
 // one sequence's keys: currents[H(key) % pool] += 1, touched[idx] = 1, counts[key] += 1
@@ -218,6 +228,24 @@ hipError_t enum_delta_ones(const unsigned long long *meta, uint64_t *out_keys, u
 constexpr int kSpecLds = 8192;
 hipError_t enum_spectrum(const uint32_t *cnt, const unsigned long long *n, size_t max_n,
                          uint32_t n_bins, unsigned long long *hist, hipStream_t s);
+
+// ---- read abundance query (nk_query.hip): nk_query_abundance(_device) ----------
+// cov[p] = the count (table + delta, as exact_lookup2) of the window starting
+// at base p of `in` (in.tile_rec for kTile tiles), NK_COV_NONE where none
+// starts; w128: t is the sorted NK_KMER_128 table (no delta)
+hipError_t query_coverage(const KmerInput &in, int k, int canonical, bool w128, const TableView &t,
+                          const DeltaArgs &d, uint32_t *cov, hipStream_t s);
+// st[r] from cov for every record (min_count >= 1).  Scratch: mid_list /
+// long_list of query_mid_cap / query_long_cap record indices (records past
+// NK_QUERY_WAVE_MAX / NK_QUERY_BLOCK_MAX windows), ctr[2], long_acc of
+// query_long_bytes bytes.  n_recs < 2^32.
+size_t query_mid_cap(size_t n_recs, size_t n_bases);
+size_t query_long_cap(size_t n_recs, size_t n_bases);
+size_t query_long_bytes(size_t n_recs, size_t n_bases);
+hipError_t query_stats(const uint64_t *offs, size_t n_recs, size_t n_bases, int k,
+                       uint32_t min_count, const uint32_t *cov, nk_read_stats *st,
+                       uint32_t *mid_list, uint32_t *long_list, unsigned long long *ctr,
+                       void *long_acc, hipStream_t s);
 
 // uniques column of the top rows from kmer_per_neuron
 hipError_t exact_top_uniques(const TopCand *cand, uint32_t m, const uint32_t *kpn, uint32_t *uniq,

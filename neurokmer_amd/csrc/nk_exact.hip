@@ -234,14 +234,6 @@ __global__ void k_top_uniques(const TopCand *__restrict__ cand, uint32_t m,
   if (i < m) uniq[i] = kpn[cand[i].idx];
 }
 
-constexpr unsigned long long kDEmpty = ~0ULL;
-
-__device__ __forceinline__ uint64_t dmix(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
-  z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
-  return z ^ (z >> 31);
-}
-
 // counts[key] += v in the delta; returns true if the key was new to the delta
 __device__ bool delta_add(const DeltaArgs &d, uint64_t key, uint32_t v) {
   if (key == kDEmpty) return atomicAdd(&d.meta[0], (unsigned long long)v) == 0;

@@ -7,6 +7,7 @@
 //   nk_export.cpp       the multi-GPU finish pieces (wire, export, merge, slices)
 //   nk_table_host.cpp   the exact k-mer table, process_sequence, extended top rows
 //   nk_enum_host.cpp    the table listed: export of (key, count) pairs, abundance spectrum
+//   nk_query_host.cpp   sequences against the table: coverage and per-record statistics
 //   nk_ingest_host.cpp  file ingest (device FASTA/FASTQ parse, host FASTQ extraction)
 // Mirrors SpikingKmerCounter (src/spiking_hash.rs:16-715) with all per-neuron
 // state resident in HBM of one MI355X:
@@ -249,6 +250,15 @@ struct nk_counter {
   DevBuf<uint32_t> en_c0, en_c1, en_c2;
   DevBuf<unsigned long long> en_wg, en_n, en_hist;
   DevBuf<uint8_t> en_tmp;
+  // read abundance query (nk_query_host.cpp), apart from the retained input
+  // (in_bases / in_offs stay the last process call's): the host variant's copy
+  // of the query, tile -> first record, coverage (also when the caller wants
+  // statistics only) and statistics, the records past each class limit,
+  // [0] / [1] their numbers, the long class's accumulators
+  DevBuf<uint8_t> q_bases, q_stats, q_acc;
+  DevBuf<uint64_t> q_offs;
+  DevBuf<uint32_t> q_trec, q_cov, q_mid, q_long;
+  DevBuf<unsigned long long> q_ctr;
   // [0] keys of the last input (sorted build) / of a process_sequence record,
   // [1] table entries (sorted: distinct keys; grouped: span + side part),
   // [2] grouped: first index of the side part, [3] side part's entries,
